@@ -18,8 +18,17 @@ Transports (the HEADLINE number is the deployable shape):
            apiserver) and the default headline.
   inproc — everything in one process against the in-memory store (upper bound; also
            reported so the wire overhead is visible).
-Default --transport both runs inproc first, then http, and reports http as the
-headline with the inproc numbers nested under "inproc".
+A plain run does only what the headline needs: the http transport, primed, warmed
+up and timed. --full adds everything else the benchmark reports: the inproc pass
+(run first, nested under "inproc"), the host calibration record and, on multi-rank
+runs, the RCCL all-reduce bus bandwidth.
+
+--dump-outputs DIR writes what the last timed step produced as DIR/<name>.npy
+(float32): gang_gpu_ids, the GPU ids the scheduler assigned to each gang of that
+step, and payload_gemm, the pod payload's product. The payload itself draws unseeded
+inputs and discards its product, so payload_gemm is the same kernel at the same
+shape run once more on inputs from a fixed seed: two builds given the same
+arguments are comparable output for output.
 
 Distributed layout (torchrun, one rank per GPU): rank 0 runs the control plane + the
 node agent for GPU 0; every rank serves a dispatch loop over a gloo control group and
@@ -34,9 +43,11 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
 import threading
 import time
 from typing import Any, Dict, List, Optional, Tuple
@@ -273,8 +284,8 @@ class HttpPlane:
     def __init__(self, args, n_gpus: int):
         port = _free_port()
         self.base = f"http://127.0.0.1:{port}"
-        cfg_path = os.path.join(REPO, "gpurun_out", f".bench_op_{port}.yaml")
-        os.makedirs(os.path.dirname(cfg_path), exist_ok=True)
+        self._cfg_dir = tempfile.mkdtemp(prefix="grove-bench-")
+        cfg_path = os.path.join(self._cfg_dir, "operator.yaml")
         with open(cfg_path, "w") as f:
             f.write("servers:\n"
                     f"  api: {{enabled: true, host: 127.0.0.1, port: {port}}}\n"
@@ -394,6 +405,7 @@ class HttpPlane:
             self.operator.wait(timeout=10)
         except subprocess.TimeoutExpired:
             self.operator.kill()
+        shutil.rmtree(self._cfg_dir, ignore_errors=True)
 
 
 def _calibrate() -> Dict[str, Any]:
@@ -437,9 +449,17 @@ def main() -> None:
     ap.add_argument("--inflight", type=int, default=2,
                     help="pipelined steps kept in flight (1 = fully serial)")
     ap.add_argument("--transport", choices=("both", "http", "inproc"),
-                    default="both",
-                    help="both = inproc + http (http is the headline)")
+                    default=None,
+                    help="both = inproc + http (http is the headline); default: "
+                         "http, or both with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the inproc "
+                         "pass, host calibration, RCCL bus bandwidth")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.transport is None:
+        args.transport = "both" if args.full else "http"
 
     comm = Comm()
     n_gpus = args.gpus or comm.world
@@ -520,6 +540,8 @@ def _drive(plane, comm: Comm, args, gang_size: int,
     """Prime + warm up + run the timed region on one control plane; return metrics."""
     tracker = plane.tracker
     world = comm.world
+    # pod name -> dispatched task, kept only for --dump-outputs
+    placed: Optional[Dict[str, Task]] = {} if args.dump_outputs else None
 
     def dispatch_cycle(idle_sleep: float = 0.0015) -> int:
         tasks = plane.drain()
@@ -529,6 +551,8 @@ def _drive(plane, comm: Comm, args, gang_size: int,
         assign: Dict[int, list] = {}
         for t in tasks:
             gpu = t[2]
+            if placed is not None:
+                placed[t[1]] = t
             rank = gpu % max(1, world)
             assign.setdefault(rank, []).append(t)
         if comm.dist is not None:
@@ -618,7 +642,15 @@ def _drive(plane, comm: Comm, args, gang_size: int,
     ttr = [(t.running - t.submitted) * 1000 for t in timed_gangs if t.running]
     tts = [(t.scheduled - t.submitted) * 1000 for t in timed_gangs if t.scheduled]
     n_gangs = args.steps * args.gangs_per_step
+    last_step_tasks = None
+    if placed is not None:
+        # per gang of the last timed step, the tasks its pods were dispatched as
+        last_step_tasks = [
+            [placed[pod] for pod in
+             tracker.gang_pods(f"bench-timed-{args.steps - 1}-{g}")]
+            for g in range(args.gangs_per_step)]
     return {
+        "last_step_tasks": last_step_tasks,
         "transport": plane.transport,
         "value": round(n_gangs / elapsed, 3),
         "elapsed_s": round(elapsed, 4),
@@ -628,6 +660,53 @@ def _drive(plane, comm: Comm, args, gang_size: int,
         "p50_time_to_scheduled_ms": round(percentile(tts, 50), 3) if tts else None,
         "rccl_allreduce_busbw_gbps": round(rccl_busbw, 1) if rccl_busbw else None,
     }
+
+
+DUMP_SEED = 20240517
+DUMP_MAX_ELEMS = 12 * 1024 * 1024  # 48 MB of float32 per array
+
+
+def _dump_outputs(out_dir: str, last_step_tasks: List[List[Task]]) -> None:
+    """Write the last timed step's outputs as <out_dir>/<name>.npy (float32).
+
+    gang_gpu_ids is what the step computed: the GPU each pod of each gang was
+    dispatched to. payload_<kind> is NOT the array the pods computed: the payloads
+    (gpunode.run_payload_descriptor -> burn_gemm / burn_decode) draw unseeded inputs
+    and discard their product, so the dump replays the extension's entry point for
+    the dispatched kind and dims (as parse_payload gave them) on seeded inputs. It
+    follows a change of the payload's kind or shape and of the kernel behind that
+    entry point, but not a change of how run_payload_descriptor calls the kernel
+    (another entry point, a non-default map_mode): keep the two in step. The stream
+    payload has no entry point that returns its array, so it has no product file.
+    """
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "gang_gpu_ids.npy"),
+            np.asarray([sorted(t[2] for t in gang) for gang in last_step_tasks],
+                       dtype=np.float32))
+    if not torch.cuda.is_available():
+        return  # the CPU development payload has no native kernel to replay
+    kind, dims = last_step_tasks[0][0][3:5]
+    ext = gpunode.load_gpuwork()
+    # inputs drawn on the host, so that they do not depend on the device generator
+    gen = torch.Generator().manual_seed(DUMP_SEED)
+
+    def draw(*shape):
+        return torch.randn(*shape, generator=gen).to(torch.bfloat16).cuda()
+
+    if kind == "gemm":
+        m, n, k, _iters = dims
+        out = ext.mfma_gemm_bf16(draw(m, k), draw(n, k))
+    elif kind == "decode":
+        n, k, _iters = dims
+        out = ext.decode_gemv(draw(n, k), draw(k))
+    else:
+        return
+    torch.cuda.synchronize()
+    if out.numel() > DUMP_MAX_ELEMS:
+        idx = torch.randint(out.numel(), (DUMP_MAX_ELEMS,), generator=gen)
+        out = out.flatten()[idx.to(out.device)]
+    np.save(os.path.join(out_dir, f"payload_{kind}.npy"), out.cpu().numpy())
 
 
 def _run_rank0(comm: Comm, args, n_gpus: int, gang_size: int) -> None:
@@ -652,7 +731,8 @@ def _run_rank0(comm: Comm, args, n_gpus: int, gang_size: int) -> None:
         plane = (InprocPlane if transport == "inproc" else HttpPlane)(args, n_gpus)
         try:
             results[transport] = _drive(plane, comm, args, gang_size,
-                                        collect_busbw=(i == len(order) - 1))
+                                        collect_busbw=(args.full and
+                                                       i == len(order) - 1))
         finally:
             plane.stop()
 
@@ -677,7 +757,6 @@ def _run_rank0(comm: Comm, args, n_gpus: int, gang_size: int) -> None:
         "p50_time_to_running_ms": headline["p50_time_to_running_ms"],
         "p95_time_to_running_ms": headline["p95_time_to_running_ms"],
         "p50_time_to_scheduled_ms": headline["p50_time_to_scheduled_ms"],
-        "calibration": _calibrate(),
         "config": {
             "model": "gang-scheduled inference PodCliqueSet (1 clique, "
                      f"{gang_size} pods x 1 amd.com/gpu, MFMA bf16 GEMM payload)",
@@ -700,6 +779,10 @@ def _run_rank0(comm: Comm, args, n_gpus: int, gang_size: int) -> None:
             "value", "ms_per_step", "p50_time_to_running_ms",
             "p95_time_to_running_ms", "p50_time_to_scheduled_ms")}
         result["inproc"]["unit"] = "gangs/s"
+    if args.full:
+        result["calibration"] = _calibrate()
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, headline["last_step_tasks"])
     print(json.dumps(result), flush=True)
 
 

@@ -105,6 +105,11 @@ class Tracker:
             if tl.scheduled is None and cond.condition_true(pg, c.PODGANG_COND_SCHEDULED):
                 tl.scheduled = now
 
+    def gang_pods(self, name: str) -> List[str]:
+        """Names of the gang's pods seen Ready (membership by the podgang label)."""
+        with self._lock:
+            return sorted(self._pod_ready.get(name, {}))
+
     def stop(self) -> None:
         self._stop.set()
         for w in self._watches:

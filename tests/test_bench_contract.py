@@ -25,7 +25,7 @@ def _last_json_line(out: str):
 @pytest.mark.timeout(240)
 def test_bench_single_rank():
     out = subprocess.run(
-        [sys.executable, "bench.py", "--steps", "3", "--warmup", "1"],
+        [sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full"],
         cwd=REPO, capture_output=True, text=True, timeout=220)
     assert out.returncode == 0, out.stderr[-2000:]
     res = _last_json_line(out.stdout)
@@ -65,10 +65,61 @@ def test_bench_two_ranks_gloo():
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29517", "bench.py", "--gpus", "2",
-         "--steps", "3", "--warmup", "1"],
+         "--steps", "3", "--warmup", "1", "--full"],
         cwd=REPO, capture_output=True, text=True, timeout=280, env=env)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
     res = _last_json_line(out.stdout)
     assert res["n_gpus"] == 2
     assert res["config"]["gang_size"] == 2
     assert res["value"] > 0
+
+
+@pytest.mark.timeout(240)
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times only the headline (wire) plane; --dump-outputs writes the
+    last timed step's placements, one row of sorted GPU ids per gang."""
+    import numpy as np
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
+         "--gangs-per-step", "3", "--dump-outputs", str(tmp_path / "out")],
+        cwd=REPO, capture_output=True, text=True, timeout=220)
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = _last_json_line(out.stdout)
+    for f in REQUIRED_FIELDS:
+        assert f in res, f"missing field {f}"
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    assert res["config"]["transport"] == "http"
+    assert "inproc" not in res and "calibration" not in res
+    ids = np.load(tmp_path / "out" / "gang_gpu_ids.npy")
+    assert ids.dtype == np.float32 and ids.shape == (3, 2)
+    # a gang of 2 on the 2-GPU node holds each GPU once
+    assert (ids == np.array([0.0, 1.0], dtype=np.float32)).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(240)
+def test_bench_dumps_payload_product(tmp_path):
+    """payload_gemm.npy is the payload kernel's product at the payload shape on the
+    seeded inputs: within the fp32-accumulation bound K * 2^-24 * |A| @ |B|^T of the
+    float64 product of the same bf16-rounded inputs."""
+    import numpy as np
+    import torch
+    import bench
+    m, n, k = 256, 384, 512
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0",
+         "--payload", f"{m}x{n}x{k}x1", "--dump-outputs", str(tmp_path)],
+        cwd=REPO, capture_output=True, text=True, timeout=220)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = np.load(tmp_path / "payload_gemm.npy")
+    assert got.dtype == np.float32 and got.shape == (m, n)
+    gen = torch.Generator().manual_seed(bench.DUMP_SEED)
+    a = torch.randn(m, k, generator=gen).to(torch.bfloat16).double()
+    bt = torch.randn(n, k, generator=gen).to(torch.bfloat16).double()
+    ref = a @ bt.t()
+    bound = k * 2.0 ** -24 * (a.abs() @ bt.abs().t())
+    err = (torch.from_numpy(got).double() - ref).abs()
+    print(f"max err {err.max().item():.3e}, min slack {(bound - err).min().item():.3e}")
+    assert (err <= bound).all()
+    ids = np.load(tmp_path / "gang_gpu_ids.npy")
+    assert ids.dtype == np.float32 and ids.shape == (4, 1) and (ids == 0).all()

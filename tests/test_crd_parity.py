@@ -1,6 +1,8 @@
 """CRD surface parity: every field in the reference CRD schemas must be implemented
 (declared in grove_amd/api/schema.py), passed through (embedded upstream types), or
-listed in KNOWN_GAPS with a reason. Runs only where /root/reference is mounted."""
+listed in KNOWN_GAPS with a reason. The tests that read the reference CRDs are marked
+`reference` and run only where the reference tree is mounted; the others run
+everywhere."""
 import functools
 import glob
 
@@ -8,8 +10,6 @@ import pytest
 import yaml
 
 from grove_amd.api.schema import SCHEMAS, KNOWN_GAPS, declared_paths
-
-pytestmark = pytest.mark.reference
 
 CRD_GLOBS = [
     "/root/reference/operator/api/core/v1alpha1/crds/*.yaml",
@@ -48,11 +48,13 @@ def _crds():
     return out
 
 
+@pytest.mark.reference
 def test_all_reference_crds_covered():
     crds = _crds()
     assert set(crds) == set(SCHEMAS), "CRD inventory mismatch"
 
 
+@pytest.mark.reference
 @pytest.mark.parametrize("crd_name", sorted(SCHEMAS))
 def test_crd_fields_implemented(crd_name):
     crds = _crds()
@@ -73,6 +75,7 @@ def test_crd_fields_implemented(crd_name):
         + "\n  ".join(missing[:40]))
 
 
+@pytest.mark.reference
 @pytest.mark.parametrize("crd_name", sorted(SCHEMAS))
 def test_crd_versions_and_scope(crd_name):
     crds = _crds()
@@ -138,6 +141,7 @@ def _deep_diff(a, b, path=""):
     return out
 
 
+@pytest.mark.reference
 @pytest.mark.parametrize("crd_name", sorted(SCHEMAS))
 def test_crd_schema_byte_compatible(crd_name):
     """The rendered CRD is semantically identical to the reference's generated YAML:
