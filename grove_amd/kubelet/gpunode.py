@@ -2,13 +2,18 @@
 
 The scheduler assigns each GPU pod device indices via the scheduling.amd.com/gpu-ids
 annotation (the amdgpu-device-plugin analog); this agent executes the pod's payload on
-that device using the native _gpuwork kernels (MFMA bf16 GEMM + HBM stream). On a GPU
-box the native extension is REQUIRED — a missing .so raises instead of silently falling
-back to eager PyTorch.
+that device using the native _gpuwork kernels (MFMA bf16 GEMM, HBM stream, decode GEMV,
+batched decode skinny GEMM). On a GPU box the native extension is REQUIRED — a missing
+.so raises instead of silently falling back to eager PyTorch.
 
 Payload spec comes from pod annotations:
-  grove.io/payload       = "gemm" (default) | "stream" | "none"
-  grove.io/payload-shape = "MxNxK[xiters]" for gemm, bytes for stream
+  grove.io/payload       = "gemm" (default) | "stream" | "decode" | "decode_batch"
+                           | "none" (any other value also runs nothing)
+  grove.io/payload-shape = gemm:         "MxNxK[xiters]"   (default 1024x1024x1024x1)
+                           stream:       "FLOATS[xiters]"  (default 16777216x2)
+                           decode:       "NxK[xiters]"     (default 8192x8192x4)
+                           decode_batch: "NxKxB[xiters]"   (default 16384x8192x16x4)
+parse_payload_shape() is the one parser of that grammar; the pod runner uses it too.
 """
 from __future__ import annotations
 
@@ -45,22 +50,46 @@ def load_gpuwork():
     return ext
 
 
-def parse_payload(pod: Obj) -> Tuple[str, Tuple[int, ...]]:
-    ann = pod["metadata"].get("annotations") or {}
-    kind = ann.get(PAYLOAD_ANNOTATION, "gemm")
-    shape = ann.get(PAYLOAD_SHAPE_ANNOTATION, "")
+PAYLOAD_KINDS = ("gemm", "stream", "decode", "decode_batch")
+
+
+def parse_payload_shape(kind: str, shape: str) -> Tuple[int, ...]:
+    """Dims of a payload-shape string for one of PAYLOAD_KINDS (the one parser shared
+    by the in-process kubelet hook and the pod runner). An empty shape gives the
+    kind's default; a missing trailing iters field defaults to 1."""
     if kind == "gemm":
         dims = tuple(int(x) for x in shape.split("x")) if shape else (1024, 1024, 1024, 1)
         if len(dims) == 3:
             dims = dims + (1,)
-        return "gemm", dims
+        return dims
     if kind == "stream":
-        return "stream", (int(shape) if shape else 1 << 24, 2)
+        # "N" -> (N, 2) as ever; "NxI" is the pod runner's long-standing iters form
+        dims = tuple(int(v) for v in shape.split("x")) if shape else (1 << 24,)
+        if len(dims) == 1:
+            dims = dims + (2,)
+        return dims
     if kind == "decode":
         dims = tuple(int(v) for v in shape.split("x")) if shape else (8192, 8192, 4)
         if len(dims) == 2:
             dims = dims + (1,)
-        return "decode", dims
+        return dims
+    if kind == "decode_batch":
+        dims = tuple(int(v) for v in shape.split("x")) if shape else (16384, 8192, 16, 4)
+        if len(dims) == 3:
+            dims = dims + (1,)
+        if len(dims) != 4:
+            raise ValueError(
+                f"decode_batch payload-shape must be NxKxB[xiters], got {shape!r}")
+        return dims
+    raise ValueError(f"unknown payload kind {kind!r}")
+
+
+def parse_payload(pod: Obj) -> Tuple[str, Tuple[int, ...]]:
+    ann = pod["metadata"].get("annotations") or {}
+    kind = ann.get(PAYLOAD_ANNOTATION, "gemm")
+    shape = ann.get(PAYLOAD_SHAPE_ANNOTATION, "")
+    if kind in PAYLOAD_KINDS:
+        return kind, parse_payload_shape(kind, shape)
     return "none", ()
 
 
@@ -102,6 +131,13 @@ def run_payload_descriptor(kind: str, dims: Tuple[int, ...], device: int) -> Dic
             n, k, iters = dims
             gbps = ext.burn_decode(n, k, iters)
             return {"device": device, "kind": kind, "weight_stream_gbps": gbps}
+        if kind == "decode_batch":
+            n, k, batch, iters = dims
+            gbps = ext.burn_decode_batch(n, k, batch, iters)
+            # one step streams the 2*n*k weight bytes once and emits `batch` tokens
+            return {"device": device, "kind": kind, "batch": batch,
+                    "weight_stream_gbps": gbps,
+                    "tokens_per_s": batch * gbps * 1e9 / (2.0 * n * k)}
     return {"device": device, "kind": kind}
 
 

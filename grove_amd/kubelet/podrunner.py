@@ -12,6 +12,22 @@ from __future__ import annotations
 import json
 import os
 import sys
+from typing import Optional, Tuple
+
+GEMM_DEFAULT_SHAPE = "512x512x512x1"  # a pod with no shape annotation stays small
+
+
+def payload_dims(payload: str, shape: Optional[str]) -> Tuple[int, ...]:
+    """Dims for run_payload_descriptor from the GROVE_PAYLOAD / GROVE_PAYLOAD_SHAPE
+    env contract, through the parser the in-process kubelet uses. An unset shape is
+    the runner's own small default for gemm and the kind's default otherwise; an
+    unknown kind has no dims and runs nothing."""
+    from .gpunode import PAYLOAD_KINDS, parse_payload_shape
+    if payload not in PAYLOAD_KINDS:
+        return ()
+    if not shape:
+        shape = GEMM_DEFAULT_SHAPE if payload == "gemm" else ""
+    return parse_payload_shape(payload, shape)
 
 
 def main() -> int:
@@ -38,15 +54,11 @@ def main() -> int:
         print("podrunner: startup dependencies satisfied", flush=True)
 
     payload = os.environ.get("GROVE_PAYLOAD", "gemm")
-    shape = os.environ.get("GROVE_PAYLOAD_SHAPE", "512x512x512x1")
     if payload != "none":
         from .gpunode import run_payload_descriptor
-        dims = tuple(int(x) for x in shape.split("x"))
-        if len(dims) == 3:
-            dims = dims + (1,)
+        dims = payload_dims(payload, os.environ.get("GROVE_PAYLOAD_SHAPE"))
         # HIP_VISIBLE_DEVICES is set by the kubelet → device 0 is OUR gpu
-        metrics = run_payload_descriptor("gemm" if payload == "gemm" else payload,
-                                         dims, 0)
+        metrics = run_payload_descriptor(payload, dims, 0)
         print("podrunner: payload done", json.dumps(metrics), flush=True)
     return 0
 

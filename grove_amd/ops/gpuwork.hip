@@ -18,9 +18,20 @@
 //     MFMAs) measured +15% @4096³ (975 → 1124 TF/s); a 128x256/BK=32 2-WG/CU
 //     variant and bare s_setprio both REGRESSED (experiments/gemm_exp.hip).
 //   * stream_triad — float4 HBM streaming (bandwidth probe + memory-heavy payload).
+//   * decode_gemv — batch-1 decode step, y[N] = W[N,K]·x[K]: weights straight to
+//     VGPRs, scalar FMAs, shuffle reduction.
+//   * decode_gemm_bf16 — batched decode step, y[B,N] = x[B,K]·W[N,K]^T for B <= 64
+//     (skinny GEMM on v_mfma_f32_16x16x32_bf16): weights stream once per step for
+//     the whole batch, straight to VGPRs (no LDS staging); split-K across the four
+//     waves of a workgroup, combined through LDS in a fixed order; 1, 2 or 4
+//     weight-row tiles per wave so that X fragments are reused from registers.
+//     Measured (1xMI355X, N=32768 K=8192): 5.4 TB/s at B=1, 4.7 at B=16, 3.2 at
+//     B=64 — docs/benchmarks.md, profiles/decode_batch_vs_hipblaslt.txt.
 //
 // Numerics: tests/test_gpu_kernels.py checks both tilings against a torch fp32
-// reference (A=I + asymmetric-B layout traps included).
+// reference (A=I + asymmetric-B layout traps included);
+// tests/test_gpu_decode_batch.py checks decode_gemm_bf16 (one-hot W layout trap,
+// float64 reference).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
@@ -340,6 +351,222 @@ double burn_decode(int64_t n, int64_t k, int64_t iters) {
     return 2.0 * n * k * iters / secs / 1e9;  // weight bytes streamed
 }
 
+// ---------------------------------------------------------------- batched decode
+// y[b][n] = sum_k x[b][k] * W[n][k] for 1 <= B <= 64 sequences: the weights stream
+// from HBM once per step for the whole batch. One workgroup per 16*R weight rows,
+// four waves, each owning one quarter of K. W rows are the MFMA A operand and batch
+// rows the B operand of v_mfma_f32_16x16x32_bf16, so with the operand lane map
+// (row = lane&15, k = 8*(lane>>4) + j) both fragments are plain 16-B loads from
+// row-major memory: no LDS staging, no transpose. k stays in natural order, so the
+// four lanes that share a row read one contiguous 64-B piece per load and two
+// consecutive loads finish a 128-B line. (Measured: the permuted order that gives
+// each LANE a 64-B run instead — 32 lines quarter-touched per load — ran at 0.65x
+// the rate.) T = ceil(B/16) batch tiles reuse each W fragment and R = 1, 2 or 4 row
+// tiles per wave reuse each X fragment (decode_gemm_rows below), so a workgroup
+// covers 16*R weight rows. W is prefetched one 128-wide step ahead (the X loads of
+// a step issue before the next W loads, so the in-order wait for X leaves those in
+// flight). Both operands use default cache policy: non-temporal W loads measured
+// 0.92x at B=16 and 32 and 1.01x at B=1 (N=32768, K=8192, 537 MB of weights). The four
+// K-quarter partials meet in LDS and are summed in wave order: no atomics, so
+// results are bit-identical from call to call.
+using f32x4 = __attribute__((ext_vector_type(4))) float;      // 16x16 accumulator
+
+#define DG_STEP 128   // k per wave-step: 4 MFMAs x 32
+
+template <int T, int R>
+__global__ __launch_bounds__(256)
+void decode_gemm_kernel(const bf16* __restrict__ W,   // [N][K] row-major
+                        const bf16* __restrict__ X,   // [B][K] row-major
+                        float* __restrict__ Y,        // [B][N]
+                        int B, int N, int K) {
+    __shared__ f32x4 red[4 * R * T * WAVE];
+    const int lane = threadIdx.x % WAVE;
+    const int wave = threadIdx.x / WAVE;
+    const int r = lane & 15, g = lane >> 4;
+    const int kq = K / 4;                               // this wave's K slice
+    const int steps = kq / DG_STEP;
+    const long koff = (long)wave * kq + 8 * g;
+    const long n0 = (long)blockIdx.x * (16 * R);
+    const bf16* wp = W + (n0 + r) * K + koff;           // row tile q: + q * 16 * K
+    // X goes through a buffer descriptor that ends at row B: a batch-tail lane's
+    // byte offset (row b >= B) lies past num_records, so the hardware range check
+    // drops that lane's access and returns the zero fragment — no branch around
+    // the loads (per-load branches made the compiler wait vmcnt(0) and drain the
+    // W prefetch). Host side bounds K so that 64 rows fit the 32-bit offset.
+    const auto xrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<bf16*>(X), /*stride*/0, B * K * 2, 0x00020000);
+    unsigned xoff[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+        xoff[t] = (unsigned)(((long)(t * 16 + r) * K + koff) * 2);
+
+    auto load_w = [&](bf16x8 (&w)[R][4], int s) {
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const bf16x8* p = (const bf16x8*)(wp + (long)q * 16 * K + (long)s * DG_STEP);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                w[q][i] = p[4 * i];
+        }
+    };
+    auto load_x = [&](bf16x8 (&x)[T][4], int s) {
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                x[t][i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                    xrsrc, xoff[t] + s * (DG_STEP * 2) + i * 64, 0, 0));
+    };
+
+    f32x4 acc[R][T] = {};
+    auto mma = [&](const bf16x8 (&w)[R][4], const bf16x8 (&x)[T][4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int q = 0; q < R; ++q)
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+                    acc[q][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        w[q][i], x[t][i], acc[q][t], 0, 0, 0);
+    };
+
+    // two steps per trip with statically named W sets; the steady loop has no
+    // branch between a load and its use, so the wait before each MFMA group is a
+    // counted vmcnt that leaves the W prefetch in flight. The last one or two
+    // steps are peeled.
+    bf16x8 w0[R][4], w1[R][4], xf[T][4];
+    load_w(w0, 0);
+    int s = 0;
+    for (; s + 2 < steps; s += 2) {
+        load_x(xf, s);
+        load_w(w1, s + 1);
+        mma(w0, xf);
+        load_x(xf, s + 1);
+        load_w(w0, s + 2);
+        mma(w1, xf);
+    }
+    load_x(xf, s);
+    if (s + 1 < steps) {
+        load_w(w1, s + 1);
+        mma(w0, xf);
+        load_x(xf, s + 1);
+        mma(w1, xf);
+    } else {
+        mma(w0, xf);
+    }
+
+    // C/D map for 16x16: col = lane&15 -> b, row = 4*(lane>>4) + reg -> n
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+            red[((wave * R + q) * T + t) * WAVE + lane] = acc[q][t];
+    __syncthreads();
+    const int nl = threadIdx.x & 15, bl = threadIdx.x >> 4;
+    const float* redf = (const float*)red;
+    const int src = (((nl >> 2) * 16 + bl) << 2) + (nl & 3);
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            int b = t * 16 + bl;
+            if (b < B) {
+                float sum = redf[(q * T + t) * WAVE * 4 + src];
+#pragma unroll
+                for (int w = 1; w < 4; ++w)
+                    sum += redf[((w * R + q) * T + t) * WAVE * 4 + src];
+                Y[(long)b * N + n0 + q * 16 + nl] = sum;
+            }
+        }
+}
+
+static void check_decode_gemm_dims(int64_t B, int64_t N, int64_t K) {
+    TORCH_CHECK(B >= 1 && B <= 64 && N >= 16 && N % 16 == 0 && K >= 512 && K % 512 == 0
+                && N <= INT32_MAX && K <= (1 << 23),
+                "decode_gemm_bf16 requires 1<=B<=64, N%16==0, K%512==0 (got B=", B,
+                " N=", N, " K=", K, ")");
+}
+
+template <int T>
+static void launch_decode_gemm_t(const bf16* w, const bf16* x, float* y, int B, int N,
+                                 int K, int rows, hipStream_t stream) {
+    dim3 grid(N / (16 * rows)), block(256);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, w, x, y, B, N, K);
+    };
+    if (rows == 4) go(decode_gemm_kernel<T, 4>);
+    else if (rows == 2) go(decode_gemm_kernel<T, 2>);
+    else go(decode_gemm_kernel<T, 1>);
+}
+
+// Row tiles per wave. Every workgroup re-reads its K slices of X from L2, so with one
+// row tile the L2->L1 traffic is (1 + B/16) x the weight stream and caps it (measured
+// ~8.5 TB/s in all: 4.2 TB/s of weights at B=16, 1.8 at B=64). Two or four row tiles
+// per wave reuse each X fragment from registers. They pay only while the grid still
+// covers the chip: at N=4096 two tiles (128 workgroups) ran at 0.7x one tile. B <= 8
+// reads little X (batch-tail lanes fetch nothing) and keeps one tile for occupancy.
+static int decode_gemm_rows(int64_t B, int64_t N) {
+    int rows = B <= 8 ? 1 : B <= 16 ? 2 : 4;
+    while (rows > 1 && (N % (16 * rows) != 0 || N / (16 * rows) < 256))
+        rows /= 2;
+    return rows;
+}
+
+static void launch_decode_gemm(const bf16* w, const bf16* x, float* y, int64_t B,
+                               int64_t N, int64_t K, int64_t rows, hipStream_t stream) {
+    if (!rows) rows = decode_gemm_rows(B, N);
+    TORCH_CHECK((rows == 1 || rows == 2 || rows == 4) && N % (16 * rows) == 0,
+                "rows must be 0 (auto), 1, 2 or 4 and 16*rows must divide N");
+    switch ((B + 15) / 16) {
+    case 1: launch_decode_gemm_t<1>(w, x, y, B, N, K, rows, stream); break;
+    case 2: launch_decode_gemm_t<2>(w, x, y, B, N, K, rows, stream); break;
+    case 3: launch_decode_gemm_t<3>(w, x, y, B, N, K, rows, stream); break;
+    default: launch_decode_gemm_t<4>(w, x, y, B, N, K, rows, stream); break;
+    }
+}
+
+torch::Tensor decode_gemm_bf16(torch::Tensor w, torch::Tensor x) {
+    TORCH_CHECK(w.is_cuda() && x.is_cuda() && w.dtype() == torch::kBFloat16
+                && x.dtype() == torch::kBFloat16, "bf16 GPU tensors required");
+    TORCH_CHECK(w.get_device() == x.get_device(), "w and x must be on one device");
+    TORCH_CHECK(w.dim() == 2 && x.dim() == 2, "w must be [N,K] and x [B,K]");
+    TORCH_CHECK(w.is_contiguous() && x.is_contiguous(), "contiguous required");
+    int64_t N = w.size(0), K = w.size(1), B = x.size(0);
+    TORCH_CHECK(x.size(1) == K, "shape mismatch: w[N,K] x[B,K]");
+    check_decode_gemm_dims(B, N, K);
+    auto y = torch::empty({B, N}, w.options().dtype(torch::kFloat32));
+    launch_decode_gemm((const bf16*)w.data_ptr(), (const bf16*)x.data_ptr(),
+                       y.data_ptr<float>(), B, N, K, 0,
+                       at::hip::getCurrentHIPStream());
+    return y;
+}
+
+// Batched decode payload: `iters` decode steps of `batch` sequences over an [n,k]
+// weight matrix; returns weight-stream GB/s (the weights are read once per step
+// whatever the batch). rows = 1, 2 or 4 forces the row tiles per wave (0 = the
+// kernel's own choice), for measuring the variants against each other.
+double burn_decode_batch(int64_t n, int64_t k, int64_t batch, int64_t iters,
+                         int64_t rows) {
+    check_decode_gemm_dims(batch, n, k);
+    auto opt = torch::TensorOptions().dtype(torch::kBFloat16).device(torch::kCUDA);
+    auto w = torch::randn({n, k}, opt.dtype(torch::kFloat32)).to(torch::kBFloat16);
+    auto x = torch::randn({batch, k}, opt.dtype(torch::kFloat32)).to(torch::kBFloat16);
+    auto y = torch::empty({batch, n}, opt.dtype(torch::kFloat32));
+    hipStream_t stream = at::hip::getCurrentHIPStream();
+    auto launch = [&] {
+        launch_decode_gemm((const bf16*)w.data_ptr(), (const bf16*)x.data_ptr(),
+                           y.data_ptr<float>(), batch, n, k, rows, stream);
+    };
+    launch();
+    C10_HIP_CHECK(hipStreamSynchronize(stream));
+    auto t0 = std::chrono::steady_clock::now();
+    for (int64_t i = 0; i < iters; ++i) launch();
+    C10_HIP_CHECK(hipStreamSynchronize(stream));
+    auto t1 = std::chrono::steady_clock::now();
+    double secs = std::chrono::duration<double>(t1 - t0).count();
+    return 2.0 * n * k * iters / secs / 1e9;  // weight bytes streamed
+}
+
 __global__ void stream_triad_kernel(const float4* __restrict__ a,
                                     const float4* __restrict__ b,
                                     float4* __restrict__ c, long n4, float s) {
@@ -450,7 +677,8 @@ double stream_triad(int64_t n_floats, int64_t iters) {
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.doc() = "grove_amd MI355X pod-payload kernels (MFMA bf16 GEMM, HBM stream)";
+    m.doc() = "grove_amd MI355X pod-payload kernels (MFMA bf16 GEMM, HBM stream, "
+              "decode GEMV, batched decode skinny GEMM)";
     m.def("mfma_gemm_bf16", &mfma_gemm_bf16, "C[M,N]=A[M,K]@Bt[N,K]^T (bf16 in, fp32 out)");
     m.def("burn_gemm", &burn_gemm, "run iters GEMM steps; returns TFLOP/s",
           pybind11::arg("m"), pybind11::arg("n"), pybind11::arg("k"),
@@ -463,4 +691,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("decode_gemv", &decode_gemv, "y[N]=W[N,K]@x[K] (bf16 in, fp32 out)");
     m.def("burn_decode", &burn_decode,
           "iters decode GEMV steps; returns weight-stream GB/s");
+    m.def("decode_gemm_bf16", &decode_gemm_bf16,
+          "y[B,N]=x[B,K]@W[N,K]^T for 1<=B<=64, N%16==0, K%512==0 "
+          "(args w, x; bf16 in, fp32 out)");
+    m.def("burn_decode_batch", &burn_decode_batch,
+          "iters batched decode steps; returns weight-stream GB/s",
+          pybind11::arg("n"), pybind11::arg("k"), pybind11::arg("batch"),
+          pybind11::arg("iters"), pybind11::arg("rows") = 0);
 }
