@@ -3,16 +3,19 @@
 The scheduler assigns each GPU pod device indices via the scheduling.amd.com/gpu-ids
 annotation (the amdgpu-device-plugin analog); this agent executes the pod's payload on
 that device using the native _gpuwork kernels (MFMA bf16 GEMM, HBM stream, decode GEMV,
-batched decode skinny GEMM). On a GPU box the native extension is REQUIRED — a missing
+batched decode skinny GEMM, split-KV decode attention). On a GPU box the native extension is REQUIRED — a missing
 .so raises instead of silently falling back to eager PyTorch.
 
 Payload spec comes from pod annotations:
   grove.io/payload       = "gemm" (default) | "stream" | "decode" | "decode_batch"
-                           | "none" (any other value also runs nothing)
+                           | "decode_attn" | "none" (any other value also runs nothing)
   grove.io/payload-shape = gemm:         "MxNxK[xiters]"   (default 1024x1024x1024x1)
                            stream:       "FLOATS[xiters]"  (default 16777216x2)
                            decode:       "NxK[xiters]"     (default 8192x8192x4)
                            decode_batch: "NxKxB[xiters]"   (default 16384x8192x16x4)
+                           decode_attn:  "HQxHKVxCTXxB[xiters]"
+                                         query heads, KV heads, context tokens, batch
+                                         (default 64x8x8192x32x4)
 parse_payload_shape() is the one parser of that grammar; the pod runner uses it too.
 """
 from __future__ import annotations
@@ -50,7 +53,7 @@ def load_gpuwork():
     return ext
 
 
-PAYLOAD_KINDS = ("gemm", "stream", "decode", "decode_batch")
+PAYLOAD_KINDS = ("gemm", "stream", "decode", "decode_batch", "decode_attn")
 
 
 def parse_payload_shape(kind: str, shape: str) -> Tuple[int, ...]:
@@ -80,6 +83,14 @@ def parse_payload_shape(kind: str, shape: str) -> Tuple[int, ...]:
         if len(dims) != 4:
             raise ValueError(
                 f"decode_batch payload-shape must be NxKxB[xiters], got {shape!r}")
+        return dims
+    if kind == "decode_attn":
+        dims = tuple(int(v) for v in shape.split("x")) if shape else (64, 8, 8192, 32, 4)
+        if len(dims) == 4:
+            dims = dims + (1,)
+        if len(dims) != 5:
+            raise ValueError(
+                f"decode_attn payload-shape must be HQxHKVxCTXxB[xiters], got {shape!r}")
         return dims
     raise ValueError(f"unknown payload kind {kind!r}")
 
@@ -138,6 +149,15 @@ def run_payload_descriptor(kind: str, dims: Tuple[int, ...], device: int) -> Dic
             return {"device": device, "kind": kind, "batch": batch,
                     "weight_stream_gbps": gbps,
                     "tokens_per_s": batch * gbps * 1e9 / (2.0 * n * k)}
+        if kind == "decode_attn":
+            hq, hkv, ctx, batch, iters = dims
+            gbps = ext.burn_decode_attn(hq, hkv, ctx, batch, iters)
+            # one step reads K and V of every sequence once (head dim 128, bf16)
+            # and emits `batch` tokens
+            kv_bytes_per_step = 2.0 * batch * hkv * ctx * 128 * 2
+            return {"device": device, "kind": kind, "batch": batch, "context": ctx,
+                    "kv_stream_gbps": gbps,
+                    "tokens_per_s": batch * gbps * 1e9 / kv_bytes_per_step}
     return {"device": device, "kind": kind}
 
 

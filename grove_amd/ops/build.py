@@ -60,9 +60,9 @@ def build_topo(force: bool = False) -> Path:
 
 
 def build_gpuwork(force: bool = False) -> Path:
-    src = PKG / "ops" / "gpuwork.hip"
+    srcs = [PKG / "ops" / "gpuwork.hip", PKG / "ops" / "decode_attn.hip"]
     out = PKG / "ops" / "_gpuwork.so"
-    if not force and _newer(out, [src]):
+    if not force and _newer(out, srcs):
         return out
     os.environ.setdefault("PYTORCH_ROCM_ARCH", GFX_ARCH)
     build_dir = PKG / "ops" / "_build"
@@ -70,7 +70,7 @@ def build_gpuwork(force: bool = False) -> Path:
     from torch.utils import cpp_extension
     cpp_extension.load(
         name="_gpuwork",
-        sources=[str(src)],
+        sources=[str(s) for s in srcs],
         build_directory=str(build_dir),
         extra_cuda_cflags=[f"--offload-arch={GFX_ARCH}", "-O3"],
         is_python_module=False,

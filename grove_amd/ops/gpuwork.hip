@@ -27,11 +27,17 @@
 //     weight-row tiles per wave so that X fragments are reused from registers.
 //     Measured (1xMI355X, N=32768 K=8192): 5.4 TB/s at B=1, 4.7 at B=16, 3.2 at
 //     B=64 — docs/benchmarks.md, profiles/decode_batch_vs_hipblaslt.txt.
+//   * decode_attn_bf16 — split-KV GQA decode attention over a bf16 KV cache (one
+//     query token per sequence, head dim 128). The kernels and their host entry
+//     points live in decode_attn.hip; this file declares and binds them.
+//     Measured (1xMI355X, Hq=64 Hkv=8, 8192 tokens): 5.6 TB/s of KV at B=32 —
+//     docs/benchmarks.md, profiles/decode_attn_vs_sdpa.txt.
 //
 // Numerics: tests/test_gpu_kernels.py checks both tilings against a torch fp32
 // reference (A=I + asymmetric-B layout traps included);
 // tests/test_gpu_decode_batch.py checks decode_gemm_bf16 (one-hot W layout trap,
-// float64 reference).
+// float64 reference); tests/test_gpu_decode_attn.py checks decode_attn_bf16
+// (one-hot q/k layout trap, float64 softmax reference).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
@@ -676,9 +682,18 @@ double stream_triad(int64_t n_floats, int64_t iters) {
     return 12.0 * n_floats * iters / secs / 1e9;  // 3 × 4 B per element
 }
 
+// ---------------------------------------------------------------- decode attention
+// defined in decode_attn.hip
+torch::Tensor decode_attn_bf16(torch::Tensor q, torch::Tensor k_cache,
+                               torch::Tensor v_cache, torch::Tensor seq_lens,
+                               double scale, int64_t splits);
+int64_t decode_attn_splits(int64_t batch, int64_t hkv, int64_t lmax);
+double burn_decode_attn(int64_t hq, int64_t hkv, int64_t ctx, int64_t batch,
+                        int64_t iters, int64_t splits);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "grove_amd MI355X pod-payload kernels (MFMA bf16 GEMM, HBM stream, "
-              "decode GEMV, batched decode skinny GEMM)";
+              "decode GEMV, batched decode skinny GEMM, split-KV decode attention)";
     m.def("mfma_gemm_bf16", &mfma_gemm_bf16, "C[M,N]=A[M,K]@Bt[N,K]^T (bf16 in, fp32 out)");
     m.def("burn_gemm", &burn_gemm, "run iters GEMM steps; returns TFLOP/s",
           pybind11::arg("m"), pybind11::arg("n"), pybind11::arg("k"),
@@ -698,4 +713,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "iters batched decode steps; returns weight-stream GB/s",
           pybind11::arg("n"), pybind11::arg("k"), pybind11::arg("batch"),
           pybind11::arg("iters"), pybind11::arg("rows") = 0);
+    m.def("decode_attn_bf16", &decode_attn_bf16,
+          "out[B,Hq,128]=softmax(scale*q.k^T).v over k/v_cache[B,Hkv,Lmax,128] up to "
+          "seq_lens[B] (int32, on device); bf16 in, fp32 out; scale=0 -> 1/sqrt(128); "
+          "splits=0 -> automatic",
+          pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
+          pybind11::arg("seq_lens"), pybind11::arg("scale") = 0.0,
+          pybind11::arg("splits") = 0);
+    m.def("decode_attn_splits", &decode_attn_splits,
+          "KV splits decode_attn_bf16 picks for a shape",
+          pybind11::arg("batch"), pybind11::arg("hkv"), pybind11::arg("lmax"));
+    m.def("burn_decode_attn", &burn_decode_attn,
+          "iters decode-attention steps; returns KV-stream GB/s",
+          pybind11::arg("hq"), pybind11::arg("hkv"), pybind11::arg("ctx"),
+          pybind11::arg("batch"), pybind11::arg("iters"), pybind11::arg("splits") = 0);
 }
